@@ -7,9 +7,10 @@ MFMA kernels.
 
 Wraps ops/hip/conv_s1.hip. Forward and backward-data both run the MFMA
 kernel (backward-data is the same convolution with spatially-flipped,
-channel-transposed weights); the weight gradient uses
-aten.convolution_backward (MIOpen wrw) — wrw is a [64 x 64] x 200k-K
-reduction where MIOpen's split-K igemm is already reasonable.
+channel-transposed weights).  The weight gradient of the 64-channel
+5x5 runs the v4 MFMA wrw kernel (conv_wrw4.hip); every other shape uses
+aten.convolution_backward (MIOpen wrw), which wins on the small 3x3
+maps.  T2R_ENABLE_MFMA_WRW overrides the choice (_small_wrw).
 
 Weights are prepacked per call to the kernel's LDS-friendly layout
 [rs][c/16][k][24] (16 used + 8 pad for conflict-free B-fragment reads)
@@ -29,7 +30,7 @@ import torch.nn.functional as F
 
 from tensor2robot_amd import ops as ops_mod
 
-WPAD = 24
+WPAD = 24   # ops/hip/conv_tile.h WPAD; pack_weights is the test oracle
 
 
 def pack_weights(w: torch.Tensor) -> torch.Tensor:
@@ -72,87 +73,97 @@ def _supported(x: torch.Tensor, weight: torch.Tensor, stride,
           padding[0] == padding[1])
 
 
+def _conv_forward(ctx, conv, x, weight, pad):
+  """Shared forward of the MFMA Functions: channels-last, pack, launch.
+
+  `conv` is the extension entry point (conv_s1_nhwc or
+  conv_s1_nhwc_cchunk); it is kept on ctx for the dgrad.
+  """
+  ext = ops_mod.require_hip()
+  k, c, r, s = weight.shape
+  if not x.is_contiguous(memory_format=torch.channels_last):
+    x = x.contiguous(memory_format=torch.channels_last)
+  if x.requires_grad:
+    # One dispatch for both packs; the dgrad pack rides to backward.
+    wpk, wpk_b = ext.pack_conv_w_pair(weight)
+    ctx.save_for_backward(x, weight, wpk_b)
+  else:
+    wpk = ext.pack_conv_w(weight, False)
+    ctx.save_for_backward(x, weight)
+  ctx.pad = pad
+  return conv(x, wpk, k, r, s, pad)
+
+
+def _conv_dgrad(ctx, conv, dy):
+  """dx = the same conv on the flipped/transposed pack.  dy: bf16 cl."""
+  weight = ctx.saved_tensors[1]
+  k, c, r, s = weight.shape
+  if len(ctx.saved_tensors) > 2:
+    wpk_b = ctx.saved_tensors[2]
+  else:
+    wpk_b = ops_mod.require_hip().pack_conv_w(weight, True)
+  # SAME-pad duality: the dy->dx conv pad is (R-1-pad).
+  return conv(dy, wpk_b, c, r, s, r - 1 - ctx.pad)
+
+
+def _small_wrw(x, dy, weight, pad):
+  """Weight gradient of the small-channel path.  dy: bf16 cl.
+
+  Default: the v4 tr_b16 kernel for the 5x5 (measured 1.05x MIOpen,
+  profiles/); MIOpen for 3x3 (small shapes are launch/staging-bound,
+  v4 0.5x there).  T2R_ENABLE_MFMA_WRW overrides: =1 v1 LDS-accumulator,
+  =2 v2 register-accumulator, =3 v3 rs-split, =4 v4 everywhere,
+  =0/off -> MIOpen everywhere.
+
+  (A/B note: on the big-spatial G2V 3x3 64ch @ 118^2, MIOpen wrw steady
+  state is 0.074 ms vs 0.213 for the find-free im2col+GEMM recipe — 2.9x
+  faster.  Its 3.6-s first-call find is one-time and absorbed by the
+  untimed warmup, so MIOpen stays the 3x3 wrw default everywhere; the
+  engine's replay-vs-eager check guards against find-intermediate
+  kernels being baked into a graph.)
+  """
+  ext = ops_mod.require_hip()
+  k, c, r, s = weight.shape
+  mode = os.environ.get("T2R_ENABLE_MFMA_WRW", "")
+  sq35 = c == 64 and k == 64 and r == s and r in (3, 5)
+  if (mode == "" and sq35 and r == 5) or (mode == "4" and sq35):
+    # v4 emits [K,C,R,S] bf16 directly (permute+cast fused into its
+    # reduce kernel).
+    return ext.conv_s1_wrw4(x, dy, r, s, pad).to(weight.dtype)
+  if mode == "3" and sq35:
+    wrw = ext.conv_s1_wrw3
+  elif mode == "2" and sq35:
+    wrw = ext.conv_s1_wrw2
+  elif mode == "1" and c % 32 == 0:
+    wrw = ext.conv_s1_wrw     # v1: fp32 LDS-accumulated
+  else:
+    # bf16 wrw via MIOpen (an f32 upcast here cost 30% whole-step
+    # throughput).
+    return torch.ops.aten.convolution_backward(
+        dy, x, weight, None, (1, 1), (pad, pad), (1, 1), False, (0, 0),
+        1, (False, True, False))[1].to(weight.dtype)
+  # v1-v3 emit f32 [rs][c][k] -> [K,C,R,S].
+  return wrw(x, dy, r, s, pad).reshape(r, s, c, k).permute(3, 2, 0, 1) \
+      .contiguous().to(weight.dtype)
+
+
 class _MFMAConvFunction(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, x, weight, pad):
-    ext = ops_mod.require_hip()
-    k, c, r, s = weight.shape
-    if not x.is_contiguous(memory_format=torch.channels_last):
-      x = x.contiguous(memory_format=torch.channels_last)
-    if x.requires_grad:
-      # One dispatch for both packs; the dgrad pack rides to backward.
-      wpk, wpk_b = ext.pack_conv_w_pair(weight)
-    else:
-      wpk, wpk_b = ext.pack_conv_w(weight, False), None
-    y = ext.conv_s1_nhwc(x, wpk, k, r, s, pad)
-    if wpk_b is None:
-      ctx.save_for_backward(x, weight)
-    else:
-      ctx.save_for_backward(x, weight, wpk_b)
-    ctx.pad = pad
-    return y
+    return _conv_forward(ctx, ops_mod.require_hip().conv_s1_nhwc, x,
+                         weight, pad)
 
   @staticmethod
   def backward(ctx, dy):
-    ext = ops_mod.require_hip()
     x, weight = ctx.saved_tensors[:2]
-    wpk_b = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
-    k, c, r, s = weight.shape
-    dy = dy.contiguous(memory_format=torch.channels_last)
+    dy = dy.contiguous(memory_format=torch.channels_last) \
+        .to(torch.bfloat16)
     dx = dw = None
     if ctx.needs_input_grad[0]:
-      # SAME-pad duality: the dy->dx conv pad is (R-1-pad).
-      bpad = r - 1 - ctx.pad
-      if wpk_b is None:
-        wpk_b = ext.pack_conv_w(weight, True)
-      dx = ext.conv_s1_nhwc(dy.to(torch.bfloat16), wpk_b, c, r, s, bpad)
+      dx = _conv_dgrad(ctx, ops_mod.require_hip().conv_s1_nhwc, dy)
     if ctx.needs_input_grad[1]:
-      # Default: the v4 tr_b16 kernel for the 5x5 (measured 1.05x
-      # MIOpen, profiles/); MIOpen for 3x3 (small shapes are launch/
-      # staging-bound, v4 0.5x there).  T2R_ENABLE_MFMA_WRW overrides:
-      # =1 v1 LDS-accumulator, =2 v2 register-accumulator, =3 v3
-      # rs-split, =4 v4 everywhere, =0/off -> MIOpen everywhere.
-      wrw_mode = os.environ.get("T2R_ENABLE_MFMA_WRW", "")
-      sq35 = c == 64 and k == 64 and r == s and r in (3, 5)
-      default_v4 = (wrw_mode == "" and c == 64 and k == 64 and
-                    r == 5 and s == 5)
-      # (A/B note, gpurun_out/r2b_wrw_ab: on the big-spatial G2V 3x3
-      # 64ch @ 118^2, MIOpen wrw steady state is 0.074 ms vs 0.213 for
-      # the find-free im2col+GEMM recipe — 2.9x faster.  Its 3.6-s
-      # first-call find is one-time and absorbed by the untimed warmup,
-      # so MIOpen stays the 3x3 wrw default everywhere; the engine's
-      # replay-vs-eager check guards against find-intermediate kernels
-      # being baked into a graph.)
-      if default_v4 or (wrw_mode == "4" and sq35):
-        # v4 emits [K,C,R,S] bf16 directly (permute+cast fused into
-        # its reduce kernel).
-        dw = ext.conv_s1_wrw4(x, dy.to(torch.bfloat16), r, s, ctx.pad)
-        if dw.dtype != weight.dtype:
-          dw = dw.to(weight.dtype)
-      elif wrw_mode == "3" and sq35:
-        dw_f32 = ext.conv_s1_wrw3(x, dy.to(torch.bfloat16), r, s,
-                                  ctx.pad)
-        dw = dw_f32.reshape(r, s, c, k).permute(3, 2, 0, 1) \
-            .contiguous().to(weight.dtype)
-      elif wrw_mode == "2" and sq35:
-        dw_f32 = ext.conv_s1_wrw2(x, dy.to(torch.bfloat16), r, s,
-                                  ctx.pad)
-        dw = dw_f32.reshape(r, s, c, k).permute(3, 2, 0, 1) \
-            .contiguous().to(weight.dtype)
-      elif c % 32 == 0 and wrw_mode == "1":
-        # MFMA wrw v1: fp32 LDS-accumulated [rs][c][k] -> [k][c][r][s].
-        dw_f32 = ext.conv_s1_wrw(x, dy.to(torch.bfloat16), r, s,
-                                 ctx.pad)
-        dw = dw_f32.reshape(r, s, c, k).permute(3, 2, 0, 1) \
-            .contiguous().to(weight.dtype)
-      else:
-        # bf16 wrw via MIOpen (an f32 upcast here cost 30% whole-step
-        # throughput).
-        dw = torch.ops.aten.convolution_backward(
-            dy.to(torch.bfloat16), x, weight, None, (1, 1),
-            (ctx.pad, ctx.pad), (1, 1), False, (0, 0), 1,
-            (False, True, False))[1].to(weight.dtype)
+      dw = _small_wrw(x, dy, weight, ctx.pad)
     return dx, dw, None
 
 
@@ -184,36 +195,19 @@ class _BigCConvFunction(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, x, weight, pad):
-    ext = ops_mod.require_hip()
-    k, c, r, s = weight.shape
-    if not x.is_contiguous(memory_format=torch.channels_last):
-      x = x.contiguous(memory_format=torch.channels_last)
-    if x.requires_grad:
-      wpk, wpk_b = ext.pack_conv_w_pair(weight)
-    else:
-      wpk, wpk_b = ext.pack_conv_w(weight, False), None
-    y = ext.conv_s1_nhwc_cchunk(x, wpk, k, r, s, pad)
-    if wpk_b is None:
-      ctx.save_for_backward(x, weight)
-    else:
-      ctx.save_for_backward(x, weight, wpk_b)
-    ctx.pad = pad
-    return y
+    return _conv_forward(ctx, ops_mod.require_hip().conv_s1_nhwc_cchunk,
+                         x, weight, pad)
 
   @staticmethod
   def backward(ctx, dy):
     ext = ops_mod.require_hip()
     x, weight = ctx.saved_tensors[:2]
-    wpk_b = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
     k, c, r, s = weight.shape
     dy = dy.contiguous(memory_format=torch.channels_last) \
         .to(torch.bfloat16)
     dx = dw = None
     if ctx.needs_input_grad[0]:
-      bpad = r - 1 - ctx.pad
-      if wpk_b is None:
-        wpk_b = ext.pack_conv_w(weight, True)
-      dx = ext.conv_s1_nhwc_cchunk(dy, wpk_b, c, r, s, bpad)
+      dx = _conv_dgrad(ctx, ext.conv_s1_nhwc_cchunk, dy)
     if ctx.needs_input_grad[1]:
       from tensor2robot_amd.ops import gemm_conv
       col = ext.im2col_nhwc(x, r, s, ctx.pad, 1)
@@ -295,6 +289,14 @@ def _stem_supported(x, weight, stride, padding) -> bool:
           (64, 3, 6, 6) and not x.requires_grad)
 
 
+# Ordered (predicate, launcher(x, bf16 weight, pad)) dispatch list.
+_MFMA_PATHS = (
+    (_supported, _MFMAConvFunction.apply),
+    (_bigc_supported, _BigCConvFunction.apply),
+    (_stem_supported, lambda x, w, pad: _StemConvFunction.apply(x, w)),
+)
+
+
 class MFMAConv2d(nn.Conv2d):
   """Conv2d that runs the MFMA kernel on supported GPU bf16 shapes."""
 
@@ -310,25 +312,11 @@ class MFMAConv2d(nn.Conv2d):
       # the dispatch checks see the bf16 tensor (the f32 preprocess
       # output otherwise sent the 6x6 stem to MIOpen - profiles/).
       x = x.to(torch.get_autocast_dtype("cuda"))
-    if self.bias is None and _supported(x, self.weight, self.stride,
-                                        self.padding):
-      w = self.weight
-      if w.dtype != torch.bfloat16:
-        w = w.to(torch.bfloat16)
-      return _MFMAConvFunction.apply(x, w, self.padding[0])
-    if self.bias is None and _bigc_supported(x, self.weight, self.stride,
-                                             self.padding):
-      w = self.weight
-      if w.dtype != torch.bfloat16:
-        w = w.to(torch.bfloat16)
-      return _BigCConvFunction.apply(x, w, self.padding[0])
-    if self.bias is None and _stem_supported(x, self.weight, self.stride,
-                                             self.padding):
-      w = self.weight
-      if w.dtype != torch.bfloat16:
-        w = w.to(torch.bfloat16)
-      return _StemConvFunction.apply(x, w)
     if self.bias is None:
+      for supported, function in _MFMA_PATHS:
+        if supported(x, self.weight, self.stride, self.padding):
+          return function(x, self.weight.to(torch.bfloat16),
+                          self.padding[0])
       # ResNet-family shapes (C/K up to 512, stride 1/2, 1x1/3x3):
       # hand im2col/col2im + rocBLAS GEMM (ops/gemm_conv.py) instead of
       # MIOpen's helper-kernel storm on these shapes.

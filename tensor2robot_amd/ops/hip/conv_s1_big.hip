@@ -22,28 +22,22 @@
 //    the two resident WGs per CU desynchronize and cover each other's
 //    staging latency.  (A register-held T14 prefetch was tried: the
 //    compiler spills the 12 uint4 to scratch at every VGPR budget.)
-//  * fragment maps identical to conv_s1.hip (verified by mfma_probe):
-//    A row = l%32, k = (l>>5)*8+j; B col = l%32;
-//    C/D col = l&31, row = (reg&3)+8*(reg>>2)+4*(l>>5).
+//  * tile decode, MFMA step and accumulator scatter (and the fragment
+//    maps they encode) are conv_tile.h's, shared with conv_s1.hip.
 //
 // Weight image: the SAME pack_conv_w output as conv_s1.hip
 // ([rs][c16][n(K)][24]); chunks address c16 slices of it directly.
 
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
 #include <torch/extension.h>
 #include <ATen/cuda/CUDAContext.h>
 
-typedef __hip_bfloat16 bbf16_t;
-typedef __attribute__((ext_vector_type(8))) short bbf16x8;
-typedef __attribute__((ext_vector_type(16))) float bf32x16;
+#include "conv_tile.h"
 
 #define BT_H 8
 #define BT_W 16
 #define BHALO_H (BT_H + 2)     // R = 3
 #define BHALO_W (BT_W + 2)
 #define BXP 40                 // shorts per pixel row: 32 ch + 8 pad
-#define BWPAD 24               // global packed-image n-row stride
 
 #define BXTILE (BHALO_H * BHALO_W * BXP)          // 7200 shorts
 #define BWALL (9 * 2 * 64 * 16)                   // 18432 shorts
@@ -55,9 +49,9 @@ typedef __attribute__((ext_vector_type(16))) float bf32x16;
 #define BWR 9                                     // 2304/256
 
 __global__ void __launch_bounds__(256, 2)
-conv_s1_nhwc_cchunk_kernel(const bbf16_t* __restrict__ x,
-                           const bbf16_t* __restrict__ wpk,
-                           bbf16_t* __restrict__ y,
+conv_s1_nhwc_cchunk_kernel(const cbf16_t* __restrict__ x,
+                           const cbf16_t* __restrict__ wpk,
+                           cbf16_t* __restrict__ y,
                            int N, int H, int W, int C, int K, int pad,
                            int OH, int OW, int tiles_h, int tiles_w) {
   __shared__ short lds[BXTILE + BWALL];
@@ -70,13 +64,7 @@ conv_s1_nhwc_cchunk_kernel(const bbf16_t* __restrict__ x,
   const int n0 = blockIdx.y * 64;
   const int c16n_full = C >> 4;
   const int chunks = C >> 5;
-
-  long wg = blockIdx.x;
-  const int img = wg / (tiles_h * tiles_w);
-  const int trest = wg % (tiles_h * tiles_w);
-  const int th = trest / tiles_w;
-  const int tw = trest % tiles_w;
-  const int oh0 = th * BT_H, ow0 = tw * BT_W;
+  const ConvTile t = conv_tile_decode<BT_H, BT_W>(tiles_h, tiles_w);
 
   // Per-thread staging addresses are chunk-invariant except for the
   // channel offset (x: += 32 bf16) / c16 offset (w: += 2 rows): hoist
@@ -85,7 +73,7 @@ conv_s1_nhwc_cchunk_kernel(const bbf16_t* __restrict__ x,
   // spills the 12 uint4 to scratch at every VGPR budget — direct
   // staging + 2 resident WGs/CU hides the latency instead.)
   const int x_ci[BXR] = {tid, tid + 256, tid + 512};
-  const bbf16_t* x_src[BXR];
+  const cbf16_t* x_src[BXR];
   short* x_dst[BXR];
 #pragma unroll
   for (int i = 0; i < BXR; ++i) {
@@ -93,17 +81,17 @@ conv_s1_nhwc_cchunk_kernel(const bbf16_t* __restrict__ x,
     const int ch8 = ci & 3;
     const int pix = ci >> 2;
     const int hrow = pix / BHALO_W, hcol = pix % BHALO_W;
-    const int iy = oh0 - pad + hrow;
-    const int ix = ow0 - pad + hcol;
+    const int iy = t.oh0 - pad + hrow;
+    const int ix = t.ow0 - pad + hcol;
     const bool ok = ci < BXCHUNKS && iy >= 0 && iy < H && ix >= 0 &&
         ix < W;
-    x_src[i] = ok ? x + (((long)img * H + iy) * W + ix) * C + ch8 * 8
+    x_src[i] = ok ? x + (((long)t.img * H + iy) * W + ix) * C + ch8 * 8
                   : nullptr;
     x_dst[i] = (ci < BXCHUNKS) ? &xtile[pix * BXP + ch8 * 8] : nullptr;
   }
   // w staging addresses: piece i handles nrow = (tid + i*256) >> 1;
-  // the global source advances by 2*K*BWPAD per chunk (c16g += 2).
-  const bbf16_t* w_src[BWR];
+  // the global source advances by 2*K*WPAD per chunk (c16g += 2).
+  const cbf16_t* w_src[BWR];
   short* w_dst[BWR];
 #pragma unroll
   for (int i = 0; i < BWR; ++i) {
@@ -113,18 +101,15 @@ conv_s1_nhwc_cchunk_kernel(const bbf16_t* __restrict__ x,
     const int rcl = nrow >> 6;                   // rs*2 + c16l, < 18
     const int rs = rcl >> 1;
     w_src[i] = &wpk[((long)(rs * c16n_full + (rcl & 1)) * K + n0 + nn)
-                    * BWPAD + half];
+                    * WPAD + half];
     w_dst[i] = &wall[nrow * 16 + half];
   }
-  const long w_chunk_stride = 2L * K * BWPAD;    // c16g += 2
+  const long w_chunk_stride = 2L * K * WPAD;    // c16g += 2
 
-  bf32x16 acc[2];
-  acc[0] = (bf32x16){};
-  acc[1] = (bf32x16){};
-  const int mrow = lane & 31;
-  const int kgrp = lane >> 5;
-  const int prow = (wave * 32 + mrow) / BT_W;
-  const int pcol = (wave * 32 + mrow) % BT_W;
+  cf32x16 acc[2];
+  acc[0] = (cf32x16){};
+  acc[1] = (cf32x16){};
+  const int p = wave * 32 + (lane & 31);    // this lane's A-row pixel
 
   for (int cc = 0; cc < chunks; ++cc) {
     if (cc) __syncthreads();   // prior chunk's reads done: LDS writable
@@ -146,38 +131,13 @@ conv_s1_nhwc_cchunk_kernel(const bbf16_t* __restrict__ x,
 #pragma unroll
     for (int rs = 0; rs < 9; ++rs) {
       const int r = rs / 3, s = rs % 3;
-#pragma unroll
-      for (int c16 = 0; c16 < 2; ++c16) {
-        bbf16x8 a_frag = *reinterpret_cast<const bbf16x8*>(
-            &xtile[((prow + r) * BHALO_W + (pcol + s)) * BXP
-                   + c16 * 16 + kgrp * 8]);
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
-          bbf16x8 b_frag = *reinterpret_cast<const bbf16x8*>(
-              &wall[((rs * 2 + c16) * 64 + nt * 32 + mrow) * 16
-                    + kgrp * 8]);
-          acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              a_frag, b_frag, acc[nt], 0, 0, 0);
-        }
-      }
+      conv_mfma_step<2, 2>(
+          acc, xtile, (p / BT_W + r) * BHALO_W + (p % BT_W + s), BXP,
+          wall + rs * (2 * 64 * 16), 16, 64);
     }
   }
 
-  const int ocol_n = lane & 31;
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-      const int m = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
-      const int p = wave * 32 + m;
-      const int orow = oh0 + p / BT_W;
-      const int ocol = ow0 + p % BT_W;
-      if (orow < OH && ocol < OW) {
-        y[(((long)img * OH + orow) * OW + ocol) * K
-          + n0 + nt * 32 + ocol_n] = __float2bfloat16(acc[nt][reg]);
-      }
-    }
-  }
+  conv_scatter_acc<2, BT_W>(acc, y, t, OH, OW, K, n0);
 }
 
 at::Tensor conv_s1_nhwc_cchunk(at::Tensor x, at::Tensor wpk, int64_t K,
@@ -203,9 +163,9 @@ at::Tensor conv_s1_nhwc_cchunk(at::Tensor x, at::Tensor wpk, int64_t K,
   hipLaunchKernelGGL(conv_s1_nhwc_cchunk_kernel,
                      dim3(grid_x, K / 64), dim3(256), 0,
                      stream.stream(),
-                     (const bbf16_t*)x.data_ptr(),
-                     (const bbf16_t*)wpk.data_ptr(),
-                     (bbf16_t*)y.data_ptr(),
+                     (const cbf16_t*)x.data_ptr(),
+                     (const cbf16_t*)wpk.data_ptr(),
+                     (cbf16_t*)y.data_ptr(),
                      N, H, W, C, (int)K, (int)pad, OH, OW,
                      tiles_h, tiles_w);
   return y;

@@ -36,6 +36,14 @@ def test_mfma_32x32x16_bf16_layout():
     (2, 64, 14, 14, 64, 3, 0),    # block3 VALID
     (1, 64, 33, 17, 64, 5, 2),    # ragged edges
     (1, 32, 16, 16, 32, 3, 1),    # smaller C/K
+    # Every other dispatch-table entry, on a 19x21 map: two ragged tiles
+    # per axis for both the 8x16 and the 16x16 tiles.
+    (1, 48, 19, 21, 64, 3, 1),
+    (1, 16, 19, 21, 64, 3, 1),
+    (1, 16, 19, 21, 32, 3, 0),
+    (1, 32, 19, 21, 32, 5, 2),
+    (1, 48, 19, 21, 64, 5, 2),
+    (1, 16, 19, 21, 32, 5, 2),
 ])
 def test_mfma_conv_forward_matches_torch(shape):
   import torch.nn.functional as F
@@ -58,23 +66,27 @@ def test_mfma_conv_backward_matches_torch():
   import torch.nn.functional as F
   from tensor2robot_amd.ops import conv as mconv
   torch.manual_seed(0)
-  n, c, h, w, k, r, pad = 2, 64, 27, 27, 64, 3, 1
-  x = torch.randn(n, c, h, w, device="cuda").to(torch.bfloat16) \
-      .contiguous(memory_format=torch.channels_last).requires_grad_(True)
-  weight = (torch.randn(k, c, r, r, device="cuda") * 0.1).to(
-      torch.bfloat16).requires_grad_(True)
-  y = mconv._MFMAConvFunction.apply(x, weight, pad)
-  dy = torch.randn_like(y)
-  y.backward(dy)
+  for shape in [
+      (2, 64, 27, 27, 64, 3, 1),
+      (1, 32, 19, 21, 32, 5, 2),    # dgrad on a 6-deep 8-wave ring kernel
+  ]:
+    n, c, h, w, k, r, pad = shape
+    x = torch.randn(n, c, h, w, device="cuda").to(torch.bfloat16) \
+        .contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    weight = (torch.randn(k, c, r, r, device="cuda") * 0.1).to(
+        torch.bfloat16).requires_grad_(True)
+    y = mconv._MFMAConvFunction.apply(x, weight, pad)
+    dy = torch.randn_like(y)
+    y.backward(dy)
 
-  x2 = x.detach().float().requires_grad_(True)
-  w2 = weight.detach().float().requires_grad_(True)
-  F.conv2d(x2, w2, padding=pad).backward(dy.float())
-  dx_err = (x.grad.float() - x2.grad).abs().max().item()
-  dx_scale = x2.grad.abs().max().item()
-  assert dx_err < 0.03 * max(dx_scale, 1.0), (dx_err, dx_scale)
-  dw_err = (weight.grad.float() - w2.grad).abs().max().item()
-  assert dw_err < 0.03 * max(w2.grad.abs().max().item(), 1.0)
+    x2 = x.detach().float().requires_grad_(True)
+    w2 = weight.detach().float().requires_grad_(True)
+    F.conv2d(x2, w2, padding=pad).backward(dy.float())
+    dx_err = (x.grad.float() - x2.grad).abs().max().item()
+    dx_scale = x2.grad.abs().max().item()
+    assert dx_err < 0.03 * max(dx_scale, 1.0), (shape, dx_err, dx_scale)
+    dw_err = (weight.grad.float() - w2.grad).abs().max().item()
+    assert dw_err < 0.03 * max(w2.grad.abs().max().item(), 1.0), shape
 
 
 @requires_gpu
@@ -86,7 +98,7 @@ def test_mfma_conv_module_dispatch():
       .contiguous(memory_format=torch.channels_last)
   y = m(x)
   assert y.shape == (2, 64, 33, 33)
-  # 5x5 falls back to torch conv (bf16 weights cast inside).
+  # 5x5 runs the ring kernel (weights cast to bf16 by the module).
   m5 = mconv.MFMAConv2d(64, 64, 5, padding=2).cuda().to(
       memory_format=torch.channels_last)
   assert m5(x).shape == (2, 64, 33, 33)
